@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: Mpixels/s of the strict JPEG encode path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 Workload (BASELINE.json configs[1], batched so that the timed region is long enough to mean
 something): one step = ONE call of mi355_jpeg_encode_scan_device on a batch of
@@ -35,6 +35,7 @@ Prints ONE JSON line on rank 0:
                 configs[4] (one 16384x16384 q90 frame without chroma averaging), fruit.ppm tiled to 3840x2160 in strict
                 mode and in standard 4:2:0 -- secondary, never `value`.
 All outputs written in the timed region are re-verified after it (see verify_outputs).
+--dump-outputs DIR also writes what the last timed step computed as .npy files (see dump_outputs).
 """
 import argparse
 import hashlib
@@ -281,6 +282,33 @@ def ascii_sha(packed, nb):
     return hashlib.sha256((np.unpackbits(packed)[:nb] + ord("0")).astype(np.uint8).tobytes()).hexdigest()
 
 
+DUMP_SAMPLE_SEED = 1234
+DUMP_BUDGET_BYTES = 48 << 20  # all ranks together; --dump-outputs promises at most 64 MB
+
+
+def dump_outputs(dirname, out, n_bits, rank, world):
+    """--dump-outputs: what the last timed step handed its caller -- every frame's scan bit count and its packed scan
+    bytes (`out` [frames, cap] uint8, torch, any device) -- as .npy files in float64 / float32.  The packed buffer is far
+    over the size limit, so its bytes go as a fixed sample: the same seeded positions in every frame slot, with the bytes
+    past a frame's scan and the unused low bits of its last byte written as 0.  Files are prefixed rankN_ when N > 1."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    F, cap = out.shape
+    nb = np.asarray(n_bits, np.int64)
+    per_frame = max(1, min(cap, DUMP_BUDGET_BYTES // 4 // (F * world)))
+    pos = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(cap, per_frame, replace=False))
+    sample = out[:, torch.from_numpy(pos).to(out.device)].cpu().numpy().astype(np.int64)
+    nbytes = (nb + 7) // 8
+    sample[pos[None, :] >= nbytes[:, None]] = 0
+    last = pos[None, :] == nbytes[:, None] - 1
+    keep = (0xFF << ((8 - nb % 8) % 8)) & 0xFF  # bits of the last byte that belong to the scan
+    sample = np.where(last, sample & keep[:, None], sample)
+    pre = "rank%d_" % rank if world > 1 else ""
+    np.save(os.path.join(dirname, pre + "scan_n_bits.npy"), nb.astype(np.float64))
+    np.save(os.path.join(dirname, pre + "scan_bytes_sample.npy"), sample.astype(np.float32))
+    np.save(os.path.join(dirname, pre + "scan_bytes_sample_index.npy"), pos.astype(np.float64))
+
+
 # ---------------------------------------------------------------------------------------------
 # process layout
 # ---------------------------------------------------------------------------------------------
@@ -363,7 +391,7 @@ def dry_run_cpu(args):
     """TEST-ONLY rehearsal of the multi-process path on CPU (gloo): same launcher, sharding, barrier,
     timing and aggregation code as the GPU run, with the oracle standing in as the worker on
     tiny frames.  Used by tests/test_bench_distributed.py; never a benchmark result."""
-    import torch  # noqa: F401
+    import torch
     import torch.distributed as dist
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import oracle_lib as ol
@@ -378,15 +406,22 @@ def dry_run_cpu(args):
     w, h, F = 64, 48, max(1, args.frames_per_step)
     frames = lcg_frames(F, shard_seed0(rank, F), w, h)
     bits = [0] * F
+    scans = [None] * F
 
     def step(i):
         for k in range(F):
-            bits[k] = ol.oracle_encode(frames[k]).n_bits
+            o = ol.oracle_encode(frames[k])
+            bits[k], scans[k] = o.n_bits, o.bits
 
     for i in range(args.warmup):
         step(i)
     dt = timed_region(step, args.steps, dist, distributed, lambda: None)
     dt, per = gather_times(dt, dist, distributed, "cpu")
+    if args.dump_outputs:
+        out = torch.zeros((F, max(len(b) for b in scans)), dtype=torch.uint8)
+        for k, b in enumerate(scans):
+            out[k, :len(b)] = torch.from_numpy(np.asarray(b, np.uint8))
+        dump_outputs(args.dump_outputs, out, bits, rank, world)
     allbits = [None] * world
     if distributed:
         dist.all_gather_object(allbits, bits)
@@ -403,8 +438,8 @@ def dry_run_cpu(args):
         print(json.dumps({"metric": "DRY RUN (cpu oracle, gloo) -- not a benchmark", "n_gpus": world, **secondary,
                           "ranks_seen": dist.get_world_size() if distributed else 1,
                           "launcher": "bench.py" if os.environ.get("MI355_BENCH_SPAWNED") else "external",
-                          "steps": args.steps, "warmup": args.warmup, "scaling": "weak",
-                          "value": round(world * args.steps * F * w * h / dt / 1e6, 4), "unit": "Mpixel/s",
+                          "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 5),
+                          "scaling": "weak", "value": round(world * args.steps * F * w * h / dt / 1e6, 4), "unit": "Mpixel/s",
                           "per_rank_mpixel_s": [round(args.steps * F * w * h / t / 1e6, 4) for t in per],
                           "seed0_per_rank": [shard_seed0(r, F) for r in range(world)],
                           "bits_per_rank": allbits}), flush=True)
@@ -558,6 +593,8 @@ def worker(args):
     dt, per_rank = gather_times(dt, dist, distributed, coll_dev)
     _, n_gold_after = verify_outputs("after the timed region", ref_bits, ref_out)
     del ref_out
+    if args.dump_outputs:  # before the secondary legs below reuse d_out
+        dump_outputs(args.dump_outputs, d_out, ref_bits, rank, world)
     nb0 = int(ref_bits[0])
     scan0 = d_out[0, :(nb0 + 7) // 8].cpu().numpy()  # frame 0 as the timed region wrote it (the legs below reuse d_out)
 
@@ -789,6 +826,9 @@ def main():
     ap.add_argument("--verify-frames", type=int, default=4, help="frames per rank re-hashed against the reference goldens")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--quick", action="store_true", help="skip the secondary legs (latency, standard mode, end to end)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (per-frame scan bit counts and a fixed "
+                         "seeded sample of the scan bytes) as DIR/<name>.npy in float64/float32, at most 64 MB in all")
     ap.add_argument("--worker-timeout", type=float, default=1500.0)
     ap.add_argument("--dead-rank-grace", type=float, default=30.0, help=argparse.SUPPRESS)
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl", help=argparse.SUPPRESS)
@@ -796,6 +836,8 @@ def main():
     ap.add_argument("--dry-run-cpu", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--rehearse-dist", action="store_true", help=argparse.SUPPRESS)  # N = 1 through the process-group code path
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(launch_workers(args, sys.argv[1:]))
     if args.dry_run_cpu:

@@ -88,7 +88,7 @@ def ref_available():
 
 def ref():
     """The real reference stage library (built in this container from
-    /root/reference/src/utils.cpp in place).  None when not built/loadable."""
+    the reference's own utils.cpp in place).  None when not built/loadable."""
     global _ref
     if _ref is None:
         path = os.path.join(ORACLE_DIR, "_ref", "libjpegref.so")

@@ -10,6 +10,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import oracle_lib as ol
 from conftest import ROOT
 
@@ -98,3 +99,28 @@ def test_secondary_legs_are_emitted_at_every_n():
     for n in (1, 2):
         r = run_launcher_free(n)
         assert "cpu_baseline" in r and "end_to_end" in r and r["end_to_end"]["gpus"] == n
+
+
+def test_dump_outputs_writes_the_last_step(tmp_path):
+    """--dump-outputs DIR: the scan bit counts and a seeded sample of the packed scan bytes of the last timed step as
+    float .npy files, identical from run to run and equal to what the encoder computes for those frames."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    dumps = []
+    for i in range(2):
+        d = tmp_path / str(i)
+        r = parse(subprocess.run([sys.executable, BENCH, "--gpus", "1"] + ARGS + ["--dump-outputs", str(d)], env=env,
+                                 capture_output=True, text=True, timeout=300))
+        assert r["steps"] == 3 and r["ms_per_step"] > 0
+        dumps.append({n: np.load(d / (n + ".npy")) for n in ("scan_n_bits", "scan_bytes_sample", "scan_bytes_sample_index")})
+    a, b = dumps
+    for n in a:
+        assert a[n].dtype in (np.float32, np.float64) and np.array_equal(a[n], b[n]), n
+    pos = a["scan_bytes_sample_index"].astype(np.int64)
+    assert a["scan_bytes_sample"].shape == (3, pos.size)
+    for k in range(3):
+        o = ol.oracle_encode(ol.lcg_frame(64, 48, 1 + k))
+        assert a["scan_n_bits"][k] == o.n_bits
+        scan = np.packbits(np.unpackbits(np.asarray(o.bits, np.uint8))[:o.n_bits])  # unused low bits of the last byte: 0
+        packed = np.zeros(max(pos.max() + 1, scan.size), np.uint8)
+        packed[:scan.size] = scan
+        assert np.array_equal(a["scan_bytes_sample"][k], packed[pos].astype(np.float32)), k
