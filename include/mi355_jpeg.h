@@ -85,6 +85,19 @@ enum mi355_jpeg_status {
                                 in parallel).  The scan entry points return the aligned intervals WITHOUT markers
                                 (markers must not be byte-stuffed, so they are added together with the stuffing);
                                 mi355_jpeg_wrap_jfif cannot add them afterwards and refuses the flag. */
+#define MI355_F_GRAY 16u     /* with MI355_F_STANDARD only (MI355_E_ARG otherwise, and MI355_E_ARG with MI355_F_420): a
+                                one-component (grayscale) baseline JPEG.  Input: 8-bit samples, W*H bytes per frame,
+                                row-major, frames contiguous (in place of the interleaved RGB of every entry point below);
+                                geometry, mirror padding and the refusal of a pad wider than the image as in 4:4:4.  No
+                                colour conversion: the samples enter the transform as they are, with the luma quantiser
+                                and the luma DC/AC code tables only; every coefficient is the one standard 4:4:4 gives
+                                the luma of (g,g,g) (the luma row of the conversion sums to 2^15, so Y = g exactly).  The
+                                scan holds one unit per 8x8 block in raster order; mi355_jpeg_encode_jfif writes one DQT,
+                                SOF0 with one component (id 1, 0x11, table 0), DHT for luma DC and AC and a one-component
+                                SOS.  With MI355_F_RESTART an interval is 64 blocks (a one-component MCU is one block:
+                                DRI 64).  MI355_F_CDS is ignored.  Probes: mi355_jpeg_probe_samples writes W8*H8 bytes,
+                                mi355_jpeg_probe_coefficients N rows (N = blocks, scan order); mi355_jpeg_probe_unit_bits
+                                refuses the flag.  Build support: mi355_jpeg_supported_flags() & MI355_F_GRAY. */
 #define MI355_F_DEFAULT MI355_F_CDS
 
 /* One Huffman table in the form the kernels consume: index (run<<4)|size,
@@ -109,6 +122,9 @@ typedef struct mi355_jpeg_timings {
 
 /* ---- lifetime --------------------------------------------------------- */
 int mi355_jpeg_abi_version(void);
+/* The MI355_F_* bits this build understands (0x1F with MI355_F_GRAY); callers test for a flag here, the ABI version
+ * stays 4. */
+uint32_t mi355_jpeg_supported_flags(void);
 const char *mi355_jpeg_strerror(int status);
 /* Number of usable devices (0 when there is none; never fails). */
 int mi355_jpeg_device_count(void);
@@ -152,8 +168,8 @@ void mi355_jpeg_padded_size(uint32_t W, uint32_t H, uint32_t *W8, uint32_t *H8);
 /* Upper bound in bytes of one frame's packed scan bits (what to size `out` as) in strict mode and
  * standard 4:4:4 (flags without MI355_F_420 / MI355_F_RESTART). */
 size_t mi355_jpeg_scan_bound(uint32_t W, uint32_t H);
-/* The same for any flags: 4:2:0 pads to 16x16 MCUs of six units, restart intervals pad every interval
- * to a byte boundary. */
+/* The same for any flags: 4:2:0 pads to 16x16 MCUs of six units, gray has one unit per 8x8 block instead of
+ * three, restart intervals pad every interval to a byte boundary. */
 size_t mi355_jpeg_scan_bound_flags(uint32_t W, uint32_t H, uint32_t flags);
 
 /* ---- the hot path ------------------------------------------------------
@@ -189,7 +205,8 @@ int mi355_jpeg_encode_scan(mi355_jpeg_ctx *ctx, const uint8_t *rgb, uint32_t W, 
  * free device memory (at most 32 GB), otherwise as many as fit and parts take turns (a little slower:
  * a part then waits for the tail kernels of the part whose set it reuses); plus 12 bytes per tile (64
  * blocks) for every frame.  E.g. 128 4K frames at out_stride = 8 MiB: 8 parts, 5.7 GB; at out_stride =
- * mi355_jpeg_scan_bound (84 MB): 22 GB. */
+ * mi355_jpeg_scan_bound (84 MB): 22 GB.  MI355_F_GRAY: the same with units = 8x8 blocks (one per block), i.e. a
+ * third of the metadata, and at most a third of the arena (216 x units); parts are cut by pixels as for RGB. */
 #define MI355_BITS_CAPACITY UINT64_MAX        /* = MI355_E_CAPACITY for this frame */
 #define MI355_BITS_CATEGORY (UINT64_MAX - 1)  /* = MI355_E_CATEGORY for this frame (ABI 4; ABI 3 wrote UINT64_MAX for both) */
 #define MI355_BITS_FLAGGED (UINT64_MAX - 1)
@@ -219,15 +236,15 @@ int mi355_jpeg_wrap_jfif(mi355_jpeg_ctx *ctx, const uint8_t *scan, uint64_t n_bi
  * Let every stage be parity-checked like the reference's per-stage dumps. */
 /* Samples entering the transform: after performCSC, performCDS and padding
  * (utils.cpp:92-141,199-233); out: W8*H8*3 bytes interleaved like the
- * reference's padded ppm_t. */
+ * reference's padded ppm_t (MI355_F_GRAY: W8*H8 bytes, the mirror-padded input). */
 int mi355_jpeg_probe_samples(mi355_jpeg_ctx *ctx, const uint8_t *rgb, uint32_t W, uint32_t H,
                              uint32_t flags, uint8_t *out);
 /* Quantised zig-zag coefficients in the reference's row order
- * (zigzag_arr[chan*N + block][64], utils.cpp:482-558); out: 3*N*64 int16. */
+ * (zigzag_arr[chan*N + block][64], utils.cpp:482-558); out: 3*N*64 int16 (MI355_F_GRAY: N*64, row = block). */
 int mi355_jpeg_probe_coefficients(mi355_jpeg_ctx *ctx, const uint8_t *rgb, uint32_t W, uint32_t H,
                                   uint32_t flags, int16_t *out);
 /* Bits each unit contributes, scan order 3*block+chan; out: 3*N uint32.  Strict mode only
- * (MI355_E_ARG with MI355_F_STANDARD). */
+ * (MI355_E_ARG with MI355_F_STANDARD or MI355_F_GRAY). */
 int mi355_jpeg_probe_unit_bits(mi355_jpeg_ctx *ctx, const uint8_t *rgb, uint32_t W, uint32_t H,
                                uint32_t flags, uint32_t *out);
 /* Entropy-code caller-supplied coefficients (reference row order, int16) --

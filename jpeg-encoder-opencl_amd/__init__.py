@@ -22,6 +22,7 @@ F_CDS = 1
 F_STANDARD = 2  # decodable baseline JPEG (not a behaviour of the reference), see include/mi355_jpeg.h
 F_420 = 4       # with F_STANDARD: real 4:2:0 MCUs
 F_RESTART = 8   # with F_STANDARD: restart intervals of 64 MCUs (DRI/RSTm written by encode_jfif)
+F_GRAY = 16     # with F_STANDARD (not with F_420): one-component JPEG of uint8 [H,W] / [n,H,W] frames
 F_DEFAULT = F_CDS
 
 OK, E_ARG, E_NO_DEVICE, E_CAPACITY, E_CATEGORY, E_ALLOC, E_TABLE, E_INTERNAL, E_NOT_ENCODED, E_HIP = 0, -1, -2, -3, -4, -5, -6, -7, -8, -100
@@ -61,7 +62,7 @@ ABI_SYMBOLS = [
     "mi355_jpeg_pool_set_quant", "mi355_jpeg_pool_set_quality", "mi355_jpeg_pool_set_huffman", "mi355_jpeg_pool_encode", "mi355_jpeg_pool_encode_ex",
     "mi355_jpeg_pool_register", "mi355_jpeg_pool_unregister", "mi355_jpeg_pool_debug_counts",
     "mi355_jpeg_set_encode_waves", "mi355_jpeg_wrap_jfif", "mi355_jpeg_scan_bound_flags",
-    "mi355_jpeg_last_call_launches", "mi355_jpeg_screen_stats",
+    "mi355_jpeg_last_call_launches", "mi355_jpeg_screen_stats", "mi355_jpeg_supported_flags",
     # the reference's stage functions one by one (host/mi355_stage_api.cpp wraps them in the reference's signatures)
     "mi355_jpeg_stage_csc", "mi355_jpeg_stage_cds", "mi355_jpeg_stage_copy_larger", "mi355_jpeg_stage_mirror_pad",
     "mi355_jpeg_stage_to_double", "mi355_jpeg_stage_subtract", "mi355_jpeg_stage_dct", "mi355_jpeg_stage_quantize",
@@ -93,6 +94,9 @@ def lib():
         L = C.CDLL(LIB_PATH)
         vp, u32, u64p, sz = C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.c_size_t
         L.mi355_jpeg_abi_version.restype = C.c_int
+        if hasattr(L, "mi355_jpeg_supported_flags"):  # (absent from older builds loaded through MI355_JPEG_LIB)
+            L.mi355_jpeg_supported_flags.restype = C.c_uint32
+            L.mi355_jpeg_supported_flags.argtypes = []
         L.mi355_jpeg_strerror.restype = C.c_char_p
         L.mi355_jpeg_strerror.argtypes = [C.c_int]
         L.mi355_jpeg_device_count.restype = C.c_int
@@ -142,7 +146,7 @@ def lib():
         L.mi355_jpeg_pool_unregister.argtypes = [vp, vp]
         L.mi355_jpeg_pool_debug_counts.argtypes = [vp, u64p]
         for name in ABI_SYMBOLS:  # fail at load time, not at first use, if a symbol is missing
-            if os.environ.get("MI355_JPEG_LIB") and name == "mi355_jpeg_pool_set_huffman":
+            if os.environ.get("MI355_JPEG_LIB") and name in ("mi355_jpeg_pool_set_huffman", "mi355_jpeg_supported_flags"):
                 continue  # an older build in an A/B run
             getattr(L, name)
         _lib = L
@@ -167,6 +171,22 @@ def reference_huffman(table):
 
 def scan_bound(W, H, flags=0):
     return lib().mi355_jpeg_scan_bound_flags(W, H, flags)
+
+
+def supported_flags():
+    """Mask of the F_* bits the loaded library understands (F_GRAY support: supported_flags() & F_GRAY)."""
+    return int(lib().mi355_jpeg_supported_flags())
+
+
+def _gray_frames(frames):
+    """F_GRAY input: uint8 [H,W] or [n,H,W] -> (contiguous [n,H,W], n, H, W)."""
+    frames = np.ascontiguousarray(frames, np.uint8)
+    if frames.ndim == 2:
+        frames = frames[None]
+    if frames.ndim != 3:
+        raise ValueError("F_GRAY frames are uint8 [H,W] or [n,H,W], got shape %s" % (frames.shape,))
+    n, H, W = frames.shape
+    return frames, n, H, W
 
 
 class Encoder:
@@ -223,11 +243,15 @@ class Encoder:
 
     # ---- hot path, host buffers
     def encode_scan(self, rgb, flags=F_DEFAULT, cap=None):
-        """rgb: uint8 [H,W,3] or [n,H,W,3].  Returns (list of packed-bit arrays, list of bit counts)."""
-        rgb = np.ascontiguousarray(rgb, np.uint8)
-        if rgb.ndim == 3:
-            rgb = rgb[None]
-        n, H, W, _ = rgb.shape
+        """rgb: uint8 [H,W,3] or [n,H,W,3] (F_GRAY: [H,W] or [n,H,W]).  Returns (list of packed-bit arrays, list of
+        bit counts)."""
+        if flags & F_GRAY:
+            rgb, n, H, W = _gray_frames(rgb)
+        else:
+            rgb = np.ascontiguousarray(rgb, np.uint8)
+            if rgb.ndim == 3:
+                rgb = rgb[None]
+            n, H, W, _ = rgb.shape
         if cap is None:
             cap = scan_bound(W, H, flags)
         out = np.zeros((n, cap), np.uint8)
@@ -237,8 +261,11 @@ class Encoder:
         return [out[f, :(bits[f] + 7) // 8].copy() for f in range(n)], [int(b) for b in bits]
 
     def encode_jfif(self, rgb, flags=F_DEFAULT):
+        """One frame: uint8 [H,W,3] (F_GRAY: [H,W]) -> the JFIF file as bytes."""
         rgb = np.ascontiguousarray(rgb, np.uint8)
-        H, W, _ = rgb.shape
+        H, W = rgb.shape[:2]
+        if (flags & F_GRAY) and rgb.ndim != 2:
+            raise ValueError("F_GRAY: one frame is uint8 [H,W], got shape %s" % (rgb.shape,))
         cap = 2 * scan_bound(W, H, flags) + 4096
         out = np.empty(cap, np.uint8)
         n = C.c_size_t()
@@ -275,17 +302,19 @@ class Encoder:
     # ---- stage probes
     def probe_samples(self, rgb, flags=F_DEFAULT):
         rgb = np.ascontiguousarray(rgb, np.uint8)
-        H, W, _ = rgb.shape
+        H, W = rgb.shape[:2]
         W8, H8 = (W + 7) // 8 * 8, (H + 7) // 8 * 8
-        out = np.empty((H8, W8, 3), np.uint8)
+        out = np.empty((H8, W8) if flags & F_GRAY else (H8, W8, 3), np.uint8)
         _check(lib().mi355_jpeg_probe_samples(self._h, rgb.ctypes.data, W, H, flags, out.ctypes.data))
         return out
 
     def probe_coefficients(self, rgb, flags=F_DEFAULT):
         rgb = np.ascontiguousarray(rgb, np.uint8)
-        H, W, _ = rgb.shape
+        H, W = rgb.shape[:2]
         if flags & F_420:
             units = 6 * ((W + 15) // 16) * ((H + 15) // 16)
+        elif flags & F_GRAY:
+            units = ((W + 7) // 8) * ((H + 7) // 8)
         else:
             units = 3 * ((W + 7) // 8) * ((H + 7) // 8)
         out = np.empty((units, 64), np.int16)
@@ -294,7 +323,7 @@ class Encoder:
 
     def probe_unit_bits(self, rgb, flags=F_DEFAULT):
         rgb = np.ascontiguousarray(rgb, np.uint8)
-        H, W, _ = rgb.shape
+        H, W = rgb.shape[:2]
         N = ((W + 7) // 8) * ((H + 7) // 8)
         out = np.empty(3 * N, np.uint32)
         _check(lib().mi355_jpeg_probe_unit_bits(self._h, rgb.ctypes.data, W, H, flags, out.ctypes.data))
@@ -396,9 +425,12 @@ class Pool:
         return tuple(int(x) for x in c)
 
     def encode_into(self, frames, out, flags=F_DEFAULT):
-        """frames [n,H,W,3] uint8 -> out [n,cap] uint8 (both caller-owned, e.g. registered).  Returns
+        """frames [n,H,W,3] uint8 (F_GRAY: [n,H,W]) -> out [n,cap] uint8 (both caller-owned, e.g. registered).  Returns
         (bits list, per-frame status list, seconds, return code) without raising on per-frame errors."""
-        n, H, W, _ = frames.shape
+        if flags & F_GRAY:
+            n, H, W = frames.shape
+        else:
+            n, H, W, _ = frames.shape
         bits = (C.c_uint64 * n)()
         st = (C.c_int * n)()
         secs = C.c_double()
@@ -407,9 +439,12 @@ class Pool:
         return [int(b) for b in bits], [int(x) for x in st], secs.value, rc
 
     def encode(self, frames, flags=F_DEFAULT, cap=None):
-        """frames: uint8 [n,H,W,3].  Returns (out [n,cap] uint8, bits list, seconds)."""
-        frames = np.ascontiguousarray(frames, np.uint8)
-        n, H, W, _ = frames.shape
+        """frames: uint8 [n,H,W,3] (F_GRAY: [n,H,W]).  Returns (out [n,cap] uint8, bits list, seconds)."""
+        if flags & F_GRAY:
+            frames, n, H, W = _gray_frames(frames)
+        else:
+            frames = np.ascontiguousarray(frames, np.uint8)
+            n, H, W, _ = frames.shape
         if cap is None:
             cap = scan_bound(W, H)
         out = np.zeros((n, cap), np.uint8)

@@ -15,12 +15,13 @@ struct Geom {
     uint32_t flags;         // MI355_F_*
     uint32_t fast_rows;     // 1: W % 8 == 0 and the frame base is 8-byte aligned
     uint32_t passes;        // wave passes per tile: 3 (one per channel); 6 in 4:2:0 standard mode
-                            // (four luma quarter-tiles of 16 MCUs, then Cb, then Cr)
+                            // (four luma quarter-tiles of 16 MCUs, then Cb, then Cr); 1 for gray (MI355_F_GRAY)
     uint32_t nmx;           // 4:2:0 only: MCUs (16x16) per row = W8/16; there N = MCUs per frame,
                             // W8/H8 are multiples of 16 and a tile is 64 MCUs = 384 units of the scan
-    uint64_t frame_stride;  // bytes between frames = W*H*3
+    uint64_t frame_stride;  // bytes between frames = W*H*3 (gray: W*H)
 };
 inline bool is420(const Geom& g) { return g.passes == 6; }
+inline bool is_gray(const Geom& g) { return g.passes == 1; }  // MI355_F_GRAY: one component, one pass per tile
 // Per-frame verdicts in the bit-count array of a call (include/mi355_jpeg.h: MI355_BITS_*): no output for the frame.
 constexpr uint64_t kBitsCapacity = ~0ull;  // the scan does not fit the frame's output slot
 constexpr uint64_t kBitsCategory = ~1ull;  // a coefficient without a code in the tables

@@ -235,6 +235,36 @@ __device__ __forceinline__ void generic_rowpair(const uint8_t* __restrict__ f, c
     }
 }
 
+// ---- gray (MI355_F_GRAY): one byte per pixel, no colour conversion ----
+// Rows 2*gq, 2*gq+1 of block (bx,by) as two 8-byte loads (fast path: the block lies inside the image, W % 8 == 0,
+// frame base 8-aligned); 4 dwords of 4 samples each, in sample order.
+__device__ __forceinline__ void load_gray_rowpair(const uint8_t* __restrict__ f, const Geom& g, uint32_t bx, uint32_t by,
+                                                  uint32_t gq, uint32_t (&w)[4]) {
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const uint32_t off = __umul24(by * 8 + gq * 2 + r, g.W) + bx * 8;  // see load_raw_rowpair (W * H < 2^32 always)
+        const uint2 v = *reinterpret_cast<const uint2*>(f + off);
+        w[2 * r] = v.x;
+        w[2 * r + 1] = v.y;
+    }
+}
+// Edge / unaligned tiles: one sample at a time, mirror-padded like generic_rowpair (sample_generic_int).
+__device__ __forceinline__ void generic_gray_rowpair(const uint8_t* __restrict__ f, const Geom& g, uint32_t bx, uint32_t by,
+                                                     uint32_t gq, uint32_t (&pk)[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        uint32_t v = 0;
+#pragma unroll 1
+        for (int j = 0; j < 4; ++j) {
+            const int s = i * 4 + j;  // 0..15 within the row pair
+            const uint32_t px = bx * 8 + (s & 7), py = by * 8 + gq * 2 + (s >> 3);
+            const uint32_t mx = px < g.W ? px : 2 * g.W - 1 - px, my = py < g.H ? py : 2 * g.H - 1 - py;
+            v |= (uint32_t)f[my * g.W + mx] << (8 * j);
+        }
+        pk[i] = v;
+    }
+}
+
 // ---- 4:2:0 standard mode: one chroma sample = the linear form box-filtered over the 2x2 quad, rounded once ----
 // (jpeg_tables.h: kStdCsc420).
 // Raw RGB of pixel rows row0, row0+1 of MCU (mx,my): 2 x 48 bytes as twelve 8-byte loads (fast

@@ -382,7 +382,8 @@ int make_geom(uint32_t W, uint32_t H, uint32_t flags, const void* base, Geom* g)
     if (W == 0 || H == 0 || W > 65535u || H > 65535u) return MI355_E_ARG;
     if ((flags & MI355_F_420) && !(flags & MI355_F_STANDARD)) return MI355_E_ARG;  // real 4:2:0 MCUs: standard mode only
     if ((flags & MI355_F_RESTART) && !(flags & MI355_F_STANDARD)) return MI355_E_ARG;
-    const bool s420 = (flags & MI355_F_420) != 0;
+    if ((flags & MI355_F_GRAY) && (!(flags & MI355_F_STANDARD) || (flags & MI355_F_420))) return MI355_E_ARG;
+    const bool s420 = (flags & MI355_F_420) != 0, gray = (flags & MI355_F_GRAY) != 0;
     const uint32_t A = s420 ? 16 : 8;  // MCU edge
     uint32_t W8 = (W + A - 1) / A * A, H8 = (H + A - 1) / A * A;
     // the reference mirrors with `oldWidth - diff` in size_t (utils.cpp:215,226):
@@ -394,13 +395,13 @@ int make_geom(uint32_t W, uint32_t H, uint32_t flags, const void* base, Geom* g)
     g->H8 = H8;
     g->nbx = W8 / 8;
     g->nmx = W8 / 16;
-    g->passes = s420 ? 6 : 3;
+    g->passes = s420 ? 6 : (gray ? 1 : 3);
     g->N = (W8 / A) * (H8 / A);  // 8x8 blocks per channel, or 16x16 MCUs in 4:2:0
     g->tiles = (g->N + 63) / 64;
     g->flags = flags;
-    g->frame_stride = (uint64_t)W * H * 3;
-    // the fast row loads use 32-bit byte offsets inside a frame (load_raw_rowpair)
-    g->fast_rows = (W % 8 == 0) && (((uintptr_t)base & 7u) == 0) && ((uint64_t)W * H * 3u < (1ull << 32));
+    g->frame_stride = (uint64_t)W * H * (gray ? 1u : 3u);
+    // the fast row loads use 32-bit byte offsets inside a frame (load_raw_rowpair, load_gray_rowpair)
+    g->fast_rows = (W % 8 == 0) && (((uintptr_t)base & 7u) == 0) && (g->frame_stride < (1ull << 32));
     return MI355_OK;
 }
 
@@ -872,6 +873,9 @@ int guarded(F&& f) noexcept {
 extern "C" {
 
 int mi355_jpeg_abi_version(void) { return MI355_JPEG_ABI_VERSION; }
+uint32_t mi355_jpeg_supported_flags(void) {
+    return MI355_F_CDS | MI355_F_STANDARD | MI355_F_420 | MI355_F_RESTART | MI355_F_GRAY;
+}
 
 const char* mi355_jpeg_strerror(int status) {
     switch (status) {
@@ -1073,9 +1077,9 @@ size_t mi355_jpeg_scan_bound_flags(uint32_t W, uint32_t H, uint32_t flags) {
     const bool s420 = (flags & MI355_F_420) != 0;
     const uint32_t A = s420 ? 16 : 8;
     const size_t mcus = (size_t)((W + A - 1) / A) * ((H + A - 1) / A);
-    const size_t units = mcus * (s420 ? 6 : 3);
+    const size_t units = mcus * (s420 ? 6 : ((flags & MI355_F_GRAY) ? 1 : 3));
     size_t bits = units * 1727;
-    if (flags & MI355_F_RESTART) bits += ((mcus + 63) / 64) * 7;  // every interval (64 MCUs) padded to a byte
+    if (flags & MI355_F_RESTART) bits += ((mcus + 63) / 64) * 7;  // every interval (64 MCUs; gray: 64 blocks) padded to a byte
     return (bits + 7) / 8 + 8;
 }
 
@@ -1226,7 +1230,7 @@ static int probe_samples_body(mi355_jpeg_ctx* c, const uint8_t* rgb, uint32_t W,
     int e = make_geom(W, H, flags, nullptr, &g);
     if (e) return e;
     HIP_TRY(hipSetDevice(c->device));
-    size_t ob = (size_t)g.W8 * g.H8 * 3;
+    size_t ob = (size_t)g.W8 * g.H8 * (is_gray(g) ? 1 : 3);
     if ((e = ensure(c->d_in, c->in_cap, (size_t)g.frame_stride))) return e;
     if ((e = ensure(c->d_out, c->out_cap, ob))) return e;
     HIP_TRY(hipMemcpy(c->d_in, rgb, g.frame_stride, hipMemcpyHostToDevice));
@@ -1281,7 +1285,7 @@ int mi355_jpeg_probe_coefficients(mi355_jpeg_ctx* c, const uint8_t* rgb, uint32_
 static int probe_unit_bits_body(mi355_jpeg_ctx* c, const uint8_t* rgb, uint32_t W, uint32_t H, uint32_t flags,
                                uint32_t* out){
     if (!c || !rgb || !out) return MI355_E_ARG;
-    if (flags & MI355_F_STANDARD) return MI355_E_ARG;  // the per-unit size kernel codes the reference's rules only
+    if (flags & (MI355_F_STANDARD | MI355_F_GRAY)) return MI355_E_ARG;  // the per-unit size kernel codes the reference's rules only
     Geom g;
     int e = transform_to_workspace(c, rgb, W, H, flags, &g);
     if (e) return e;
@@ -1382,14 +1386,29 @@ bool dqt_fits(const mi355_jpeg_ctx* c) {
         if (c->qlum[i] > 255 || c->qchrom[i] > 255) return false;
     return true;
 }
-// header of the build-defined container: SOI, APP0, DQT x2, SOF0, DHT x4, SOS; returns its length
+// header of the build-defined container: SOI, APP0, DQT x2, SOF0, DHT x4, SOS; returns its length.  MI355_F_GRAY: one
+// component -- DQT 0, SOF0 (id 1, 0x11, Tq 0), DHT luma DC + AC, SOS (Td/Ta 0).
 size_t jfif_header(const mi355_jpeg_ctx* c, uint32_t W, uint32_t H, uint32_t flags, uint8_t* dst, size_t cap) {
     static const uint8_t zz[64] = MI355_ZIGZAG_TABLE;
+    const bool gray = (flags & MI355_F_GRAY) != 0;
     Writer w{dst, 0, cap};
     w.w(0xFFD8);
     w.w(0xFFE0), w.w(16);
     w.b('J'), w.b('F'), w.b('I'), w.b('F'), w.b(0);
     w.w(0x0101), w.b(0), w.w(1), w.w(1), w.b(0), w.b(0);
+    if (gray) {
+        w.w(0xFFDB), w.w(67), w.b(0);
+        for (int k = 0; k < 64; ++k) w.b(c->qlum[zz[k]] > 255 ? 255 : c->qlum[zz[k]]);
+        w.w(0xFFC0), w.w(11), w.b(8), w.w(H), w.w(W), w.b(1);
+        w.b(1), w.b(0x11), w.b(0);
+        dht_segment(w, 0x00, c->huff_std[0]);
+        dht_segment(w, 0x10, c->huff_std[2]);
+        if (flags & MI355_F_RESTART) w.w(0xFFDD), w.w(4), w.w(64);  // DRI: one interval = one tile of 64 blocks
+        w.w(0xFFDA), w.w(8), w.b(1);
+        w.b(1), w.b(0x00);
+        w.b(0), w.b(63), w.b(0);
+        return w.n;
+    }
     for (int t = 0; t < 2; ++t) {
         const uint32_t* q = t ? c->qchrom : c->qlum;
         w.w(0xFFDB), w.w(67), w.b(t);
@@ -1416,6 +1435,7 @@ static int wrap_jfif_body(mi355_jpeg_ctx* c, const uint8_t* scan, uint64_t n_bit
                          uint8_t* out, size_t cap, size_t* out_len){
     if (!c || !scan || !out || !out_len || W == 0 || H == 0 || W > 65535u || H > 65535u) return MI355_E_ARG;
     if ((flags & MI355_F_420) && !(flags & MI355_F_STANDARD)) return MI355_E_ARG;
+    if ((flags & MI355_F_GRAY) && (!(flags & MI355_F_STANDARD) || (flags & MI355_F_420))) return MI355_E_ARG;
     if (flags & MI355_F_RESTART) return MI355_E_ARG;  // the markers go in with the stuffing, on the device
     if (!dqt_fits(c)) return MI355_E_TABLE;
     Writer w{out, jfif_header(c, W, H, flags, out, cap), cap};
@@ -1651,7 +1671,7 @@ void pool_run(PoolWorker* w, PoolJob* j) {
         j->rc = MI355_E_NO_DEVICE;
         return;
     }
-    const size_t fbytes = (size_t)j->W * j->H * 3;
+    const size_t fbytes = (size_t)j->W * j->H * ((j->flags & MI355_F_GRAY) ? 1 : 3);  // = Geom::frame_stride
     size_t dstride = (j->out_stride + 3) & ~(size_t)3;
     if (dstride < 8) dstride = 8;
     // Work is handed out in chunks from a cursor all workers of the call share (about 256 MB of input each, less for

@@ -22,6 +22,10 @@
 // (default there) = real 16x16 MCUs, 444 = one block per component; --restart adds DRI + RSTm markers
 // every 64 MCUs.
 //
+// A binary PGM (P5, maxval 255) input is encoded as a one-component (grayscale) JFIF: standard mode only
+// (MI355_F_GRAY), --restart for DRI + RSTm every 64 blocks; --mode strict refuses it (the reference has no
+// gray path).  --batch reads *.ppm files only and skips P5 files.
+//
 // With no arguments, run from a build/ directory like the reference
 // (README.md:43, src/OpenCLProject_JpegEncoder.cpp:320): read ../data/fruit.ppm and
 // report the stage times; the reference writes no output file, this tool writes
@@ -42,8 +46,42 @@
 static void usage() {
     std::cout << "usage: mi355-jpeg in.ppm out.jpg [-q 1..100] [--mode strict|standard] [--subsample ref420|none|420|444]\n"
                  "                  [--restart] [--no-cds] [--device K] [--repeat R] [--bits file]\n"
+                 "       mi355-jpeg in.pgm out.jpg --mode standard [-q 1..100] [--restart] [--device K]   (grayscale)\n"
                  "       mi355-jpeg --batch IN_DIR OUT_DIR [-q ..] [--mode ..] [--subsample ..]   (all visible GPUs)\n"
                  "       (no arguments: ../data/fruit.ppm -> ../data/fruit.jpg, like the reference's fixed paths)\n";
+}
+
+// A P5 (gray) file -> one-component JFIF (standard mode, MI355_F_GRAY), straight through the C ABI.
+static int run_gray(const std::string& in, const std::string& out, int quality, int device, bool restart) {
+    size_t W = 0, H = 0;
+    uint8_t* px = nullptr;
+    if (readPGMImage(in.c_str(), &W, &H, &px) == -1) return 1;
+    std::cout << "Image " << in << ": " << W << " x " << H << " (gray)" << std::endl;
+    const uint32_t flags = MI355_F_STANDARD | MI355_F_GRAY | (restart ? MI355_F_RESTART : 0u);
+    mi355_jpeg_ctx* ctx = nullptr;
+    int rc = mi355_jpeg_create(device, &ctx);
+    if (!rc) rc = mi355_jpeg_set_quality(ctx, quality);
+    std::vector<uint8_t> file;
+    size_t len = 0;
+    if (!rc) {
+        file.resize(2 * mi355_jpeg_scan_bound_flags((uint32_t)W, (uint32_t)H, flags) + 4096);
+        rc = mi355_jpeg_encode_jfif(ctx, px, (uint32_t)W, (uint32_t)H, flags, file.data(), file.size(), &len);
+    }
+    mi355_jpeg_destroy(ctx);
+    free(px);
+    if (rc) {
+        std::cout << "mi355-jpeg: " << mi355_jpeg_strerror(rc) << std::endl;
+        return 1;
+    }
+    FILE* fp = fopen(out.c_str(), "wb");
+    if (!fp || fwrite(file.data(), 1, len, fp) != len) {
+        std::cout << "mi355-jpeg: cannot write " << out << std::endl;
+        if (fp) fclose(fp);
+        return 1;
+    }
+    fclose(fp);
+    std::cout << "Wrote " << out << " (" << len << " bytes, one component)" << std::endl;
+    return 0;
 }
 
 // --batch: directory in, directory out, through the multi-GPU pool
@@ -83,7 +121,8 @@ static int run_batch(const std::string& in_dir, const std::string& out_dir, int 
         while (i < files.size()) {
             ppm_t img;
             if (readPPMImage(files[i].c_str(), &img.width, &img.height, &img.data) == -1) {
-                std::cout << "  skipped (not a P6/255 file): " << files[i] << std::endl;
+                std::cout << "  skipped (not a P6/255 file; --batch does not take gray P5 files, encode those one at a time "
+                             "with --mode standard): " << files[i] << std::endl;
                 ++i;
                 continue;
             }
@@ -216,6 +255,18 @@ int main(int argc, char** argv) {
             return 2;
         }
         return run_batch(in, out, quality, mode_flags ? mode_flags : (cds ? MI355_F_CDS : 0u));
+    }
+    if (isPGMFile(in.c_str())) {
+        if (mode != "standard") {
+            std::cout << "mi355-jpeg: " << in << " is a gray (P5) file: grayscale JPEG needs --mode standard "
+                      << "(strict mode reproduces the reference, which has no gray path)" << std::endl;
+            return 1;  // (the reader's exit status for an input it does not take)
+        }
+        if (!subsample.empty() || stages || !bits_path.empty() || repeat != 1) {
+            std::cout << "mi355-jpeg: a gray (P5) input takes -q, --restart and --device only" << std::endl;
+            return 2;
+        }
+        return run_gray(in, out, quality, device, restart);
     }
     ppm_t img;
     if (readPPMImage(in.c_str(), &img.width, &img.height, &img.data) == -1) return 1;

@@ -106,7 +106,9 @@ bool ppm_token(FILE* fp, char* tok, size_t cap) {
 }
 }  // namespace
 
-int readPPMImage(const char* path, size_t* width, size_t* height, rgb_pixel_t** img) {
+namespace {
+// binary PNM of maxval 255: magic "P6" (3 bytes per pixel) or "P5" (1 byte per pixel)
+int read_pnm(const char* path, const char* magic, size_t bpp, size_t* width, size_t* height, void** img) {
     FILE* fp = fopen(path, "rb");
     if (!fp) {
         std::cout << "Error opening the file" << std::endl;
@@ -118,7 +120,7 @@ int readPPMImage(const char* path, size_t* width, size_t* height, rgb_pixel_t** 
         fclose(fp);
         return -1;
     }
-    if (strcmp(tok, "P6") != 0) {
+    if (strcmp(tok, magic) != 0) {
         std::cout << "Invalid file format" << std::endl;
         fclose(fp);
         return -1;
@@ -144,13 +146,13 @@ int readPPMImage(const char* path, size_t* width, size_t* height, rgb_pixel_t** 
         return -1;
     }
     size_t n = (size_t)w * (size_t)h;
-    rgb_pixel_t* p = (rgb_pixel_t*)malloc(n * sizeof(rgb_pixel_t));
+    void* p = malloc(n * bpp);
     if (!p) {
         std::cout << "Error allocating memory" << std::endl;
         fclose(fp);
         return -1;
     }
-    if (fread(p, sizeof(rgb_pixel_t), n, fp) != n) {
+    if (fread(p, bpp, n, fp) != n) {
         std::cout << "Error reading the file" << std::endl;
         free(p);
         fclose(fp);
@@ -161,6 +163,25 @@ int readPPMImage(const char* path, size_t* width, size_t* height, rgb_pixel_t** 
     *height = (size_t)h;
     *img = p;
     return 0;
+}
+}  // namespace
+
+int readPPMImage(const char* path, size_t* width, size_t* height, rgb_pixel_t** img) {
+    static_assert(sizeof(rgb_pixel_t) == 3, "a PPM pixel is three bytes");
+    return read_pnm(path, "P6", sizeof(rgb_pixel_t), width, height, reinterpret_cast<void**>(img));
+}
+
+int readPGMImage(const char* path, size_t* width, size_t* height, uint8_t** img) {
+    return read_pnm(path, "P5", 1, width, height, reinterpret_cast<void**>(img));
+}
+
+bool isPGMFile(const char* path) {
+    FILE* fp = fopen(path, "rb");
+    if (!fp) return false;
+    char m[2] = {0, 0};
+    const bool p5 = fread(m, 1, 2, fp) == 2 && m[0] == 'P' && m[1] == '5';
+    fclose(fp);
+    return p5;
 }
 
 int writePPMImage(const char* path, size_t width, size_t height, rgb_pixel_t* img) {

@@ -79,6 +79,10 @@ struct GPUTelemetry {
 // ---- PPM I/O (utils.cpp:11-82): same contract: 0 ok, -1 + message on stdout ------------
 int readPPMImage(const char* path, size_t* width, size_t* height, rgb_pixel_t** img);
 int writePPMImage(const char* path, size_t width, size_t height, rgb_pixel_t* img);
+// Not in the reference: the gray counterpart (binary PGM "P5", maxval 255, header tolerated like the PPM reader's),
+// W*H bytes in *img (malloc'd); 0, or -1 + message on stdout.  isPGMFile: the file starts with "P5".
+int readPGMImage(const char* path, size_t* width, size_t* height, uint8_t** img);
+bool isPGMFile(const char* path);
 void getNearest8x8ImageSize(size_t width, size_t height, size_t* newWidth, size_t* newHeight);
 
 // ---- the reference's stage functions, with the reference's signatures (utils.hpp:77-137) --------------
