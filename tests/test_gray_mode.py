@@ -21,104 +21,8 @@ jpeg_mod = importlib.import_module("jpeg-encoder-opencl_amd")
 F_STD, F_GRAY, F_420, F_RESTART = 2, 16, 4, 8
 GRAY = F_STD | F_GRAY
 
-# ---------------------------------------------------------------- Annex K luma tables (K.3 DC, K.5 AC)
-DC_BITS = [0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0]
-DC_VALS = list(range(12))
-AC_BITS = [0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7D]
-AC_VALS = [
-    0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07,
-    0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xA1, 0x08, 0x23, 0x42, 0xB1, 0xC1, 0x15, 0x52, 0xD1, 0xF0,
-    0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0A, 0x16, 0x17, 0x18, 0x19, 0x1A, 0x25, 0x26, 0x27, 0x28,
-    0x29, 0x2A, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3A, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49,
-    0x4A, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5A, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69,
-    0x6A, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7A, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89,
-    0x8A, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9A, 0xA2, 0xA3, 0xA4, 0xA5, 0xA6, 0xA7,
-    0xA8, 0xA9, 0xAA, 0xB2, 0xB3, 0xB4, 0xB5, 0xB6, 0xB7, 0xB8, 0xB9, 0xBA, 0xC2, 0xC3, 0xC4, 0xC5,
-    0xC6, 0xC7, 0xC8, 0xC9, 0xCA, 0xD2, 0xD3, 0xD4, 0xD5, 0xD6, 0xD7, 0xD8, 0xD9, 0xDA, 0xE1, 0xE2,
-    0xE3, 0xE4, 0xE5, 0xE6, 0xE7, 0xE8, 0xE9, 0xEA, 0xF1, 0xF2, 0xF3, 0xF4, 0xF5, 0xF6, 0xF7, 0xF8,
-    0xF9, 0xFA]
-
-
-def canonical(bits, vals):
-    """{symbol: (code, length)} of a BITS/HUFFVAL table (Annex C)."""
-    table, code, k = {}, 0, 0
-    for length in range(1, 17):
-        for _ in range(bits[length - 1]):
-            table[vals[k]] = (code, length)
-            code += 1
-            k += 1
-        code <<= 1
-    return table
-
-
-DC_TAB, AC_TAB = canonical(DC_BITS, DC_VALS), canonical(AC_BITS, AC_VALS)
-
-
-def entropy_code(rows):
-    """Scan bits of one-component zig-zag rows [N][64] (scan order): (packed bytes, bit count)."""
-    rows = np.asarray(rows, np.int64)
-    codes, lens = [], []
-
-    def put(sym_tab, sym, value, size):
-        c, l = sym_tab[sym]
-        v = value if value >= 0 else value + (1 << size) - 1
-        codes.append((c << size) | (v & ((1 << size) - 1)))
-        lens.append(l + size)
-
-    ac = rows[:, 1:]
-    nzb, nzk = np.nonzero(ac)
-    bounds = np.searchsorted(nzb, np.arange(len(rows) + 1))
-    nzv = ac[nzb, nzk]
-    pred = 0
-    for b in range(len(rows)):
-        d = int(rows[b, 0]) - pred
-        pred = int(rows[b, 0])
-        s = abs(d).bit_length()
-        put(DC_TAB, s, d, s)
-        last = 0  # zig-zag position of the last coded coefficient
-        for i in range(bounds[b], bounds[b + 1]):
-            k, v = int(nzk[i]) + 1, int(nzv[i])
-            run = k - last - 1
-            while run > 15:
-                put(AC_TAB, 0xF0, 0, 0)
-                run -= 16
-            s = abs(v).bit_length()
-            put(AC_TAB, (run << 4) | s, v, s)
-            last = k
-        if last != 63:
-            put(AC_TAB, 0x00, 0, 0)
-    L = np.array(lens, np.int64)
-    Cd = np.array(codes, np.int64)
-    n_bits = int(L.sum())
-    sym = np.repeat(np.arange(len(L)), L)
-    k = np.arange(n_bits) - np.repeat(np.cumsum(L) - L, L)
-    bits = ((Cd[sym] >> (L[sym] - 1 - k)) & 1).astype(np.uint8)
-    return np.packbits(bits), n_bits
-
-
-def jfif_gray(packed, n_bits, W, H, ql):
-    """One-component baseline JFIF around a scan (the builder's container, independent of the library's)."""
-    zz = ol.zigzag_order()
-    out = bytearray(b"\xff\xd8\xff\xe0\x00\x10JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")
-    out += b"\xff\xdb\x00\x43\x00" + bytes(int(ql.reshape(64)[zz[k]]) for k in range(64))
-    out += b"\xff\xc0\x00\x0b\x08" + H.to_bytes(2, "big") + W.to_bytes(2, "big") + b"\x01\x01\x11\x00"
-    for cls, bits, vals in ((0x00, DC_BITS, DC_VALS), (0x10, AC_BITS, AC_VALS)):
-        out += b"\xff\xc4" + (3 + 16 + len(vals)).to_bytes(2, "big") + bytes([cls] + bits + vals)
-    out += b"\xff\xda\x00\x08\x01\x01\x00\x00\x3f\x00"
-    nb = (n_bits + 7) // 8
-    scan = bytearray(np.asarray(packed[:nb], np.uint8).tobytes())
-    if n_bits & 7:
-        scan[-1] |= 0xFF >> (n_bits & 7)
-    out += scan.replace(b"\xff", b"\xff\x00") + b"\xff\xd9"
-    return bytes(out)
-
-
-def checker_rows(gray, ql, qc):
-    """Luma rows of the standard-mode checker on (g,g,g): the expected coefficients of the gray frame."""
-    H, W = gray.shape
-    N = ((W + 7) // 8) * ((H + 7) // 8)
-    o = ol.oracle_std_encode(np.repeat(gray[:, :, None], 3, 2), ql, qc, keep=ol.KEEP_ZIGZAG)
-    return o.zigzag[:N]
+# the builder (Annex K luma tables, entropy coder, one-component container, checker rows) lives in oracle_lib
+entropy_code, jfif_gray, checker_rows = ol.gray_entropy_code, ol.jfif_gray, ol.gray_checker_rows
 
 
 def expected(gray, quality):
